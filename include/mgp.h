@@ -39,7 +39,10 @@ extern "C" {
                                              from the image every step and return MGP_EUNSUPPORTED without a prebuilt one;
                                              mgp_train_step_p2p: timeout semantics spelled out (partial step; collective rollback is the caller's)
                                       0.4.0: + mgp_sparse_rollout_persistent / _status: mgp_sparse_rollout at K = 3, N <= 1024 runs its T
-                                             steps as ONE launch of persistent workgroups (bit-identical outputs; see there) */
+                                             steps as ONE launch of persistent workgroups (bit-identical outputs; see there)
+                                      (version unchanged) + the centralized critic and the DDPG update: mgp_critic_fwd / _bwd /
+                                             _supported / _saved_floats / _bwd_workspace, mgp_gn_relu_fwd / _bwd / _bwd_workspace,
+                                             mgp_tap_sum, mgp_ddpg_critic_loss, mgp_ddpg_policy_loss, mgp_soft_update */
 
 #define MGP_OK            0
 #define MGP_EINVAL       -1        /* bad size / null pointer / unsupported combination */
@@ -592,6 +595,66 @@ int  mgp_train_step_agg(const float* Z, const float* target, const long* idx, in
                         float* flat_param, float* flat_grad, float* m, float* v, const int* dims, int n_layers,
                         float lr, float beta1, float beta2, float eps, int* step_dev, float* loss, float* workspace,
                         int B, int K, int N, MgpP2P* comm, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Centralized critic                               reference learner/critic.py:46-87
+ *   layers = [n_s + n_a, h_1, .., 1]; per layer l: x @ gso (the one input plane broadcast over the K taps),
+ *   Conv2d(K, out, (C_in,1), stride (C_in,1)) (weight (out, K, C_in, 1): rows in (tap, channel) order), then for hidden
+ *   layers GroupNorm(out, out) (eps 1e-5, biased variance) and ReLU.
+ * mgp_critic_fwd  states (B,1,n_s,N), actions (B,1,n_a,N), gso (B,K,N,N), all contiguous -> Q (B,N).  W / bias: n_layers
+ *                 device pointers each; gamma / beta: n_layers-1 (the hidden layers' GroupNorm affine).  dims: n_layers+1
+ *                 ints, dims[0] = n_s + n_a, dims[n_layers] = 1.  saved (NULL: inference) receives
+ *                 mgp_critic_saved_floats(...) floats: per sample the input planes, then per hidden layer the pre-norm
+ *                 output (C,N), mean (C), rstd (C) and post-ReLU planes (C,N).
+ * mgp_critic_bwd  dQ (B,N) + the forward's `saved` -> dW / db (n_layers each) and dgamma / dbeta (n_layers-1) summed over the
+ *                 batch (dW == NULL: no parameter gradients; then workspace may be NULL), and/or dActions (B,n_a,N) (NULL: not
+ *                 wanted).  workspace: mgp_critic_bwd_workspace(...) floats.  Per-sample partials reduced over B in sample
+ *                 order by a second launch: no atomics, identical calls give identical bits.
+ * One workgroup per sample runs every layer with the layer planes in LDS and the K operator slices streamed from L2 / HBM.
+ * Coverage (mgp_critic_supported): dims[n_layers] == 1, N <= 1024, LDS (3 Cp + H) N floats <= 160 KiB (Cp = widest layer
+ * input rounded up to 8, H = widest output); otherwise MGP_EUNSUPPORTED -- compose mgp_agg_fwd (input planes broadcast over
+ * the taps by a zero tap stride) / mgp_dense_fwd (weight viewed (out, K C_in)) / mgp_gn_relu_fwd and their backward
+ * (mgp_agg_bwd_x, mgp_dense_bwd, mgp_gn_relu_bwd, mgp_tap_sum for dActions).
+ * ------------------------------------------------------------------------------------ */
+int  mgp_critic_supported(const int* dims, int n_layers, int B, int K, int N);
+long mgp_critic_saved_floats(const int* dims, int n_layers, int B, int K, int N);
+long mgp_critic_bwd_workspace(const int* dims, int n_layers, int B, int K, int N);
+int  mgp_critic_fwd(const float* states, const float* actions, const float* gso, const float* const* W,
+                    const float* const* bias, const float* const* gamma, const float* const* beta,
+                    const int* dims, int n_layers, int n_s, float* Q, float* saved, int B, int K, int N, void* stream);
+int  mgp_critic_bwd(const float* dQ, const float* gso, const float* saved, const float* const* W,
+                    const float* const* gamma, const int* dims, int n_layers, int n_s,
+                    float* const* dW, float* const* db, float* const* dgamma, float* const* dbeta,
+                    float* dActions, float* workspace, int B, int K, int N, void* stream);
+
+/* GroupNorm(C, C) + ReLU on (B,C,N) planes (reference critic.py:80-82; the composed critic path).
+ * mgp_gn_relu_fwd  A = relu(gamma (Y - mean) rstd + beta) per (sample, channel) over the N agents; mean / rstd (B,C) may be NULL.
+ * mgp_gn_relu_bwd  dA is (B, taps, C, N): the gradient of A is its sum over the taps.  -> dY (B,C,N); dgamma / dbeta (C)
+ *                  summed over the batch in sample order (both NULL: not wanted).  workspace: mgp_gn_relu_bwd_workspace(B, C)
+ *                  floats.  N <= 2048.
+ * mgp_tap_sum      out[b,c,n] = sum_t X[b,t,c0+c,n], X (B,T,C,N), out (B,Cs,N): dActions of the composed path. */
+int  mgp_gn_relu_fwd(const float* Y, const float* gamma, const float* beta, float* A, float* mean, float* rstd,
+                     int B, int C, int N, float eps, void* stream);
+long mgp_gn_relu_bwd_workspace(int B, int C);
+int  mgp_gn_relu_bwd(const float* dA, int taps, const float* Y, const float* A, const float* mean, const float* rstd,
+                     const float* gamma, float* dY, float* dgamma, float* dbeta, float* workspace, int B, int C, int N,
+                     void* stream);
+int  mgp_tap_sum(const float* X, float* out, int B, int T, int C, int c0, int Cs, int N, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DDPG update pieces                               reference learner/gnn_ddpg.py:93-100,191-207
+ * mgp_ddpg_critic_loss  F.mse_loss(Q (B,1,N), r + gamma notdone Q' (B,B,N)) exactly as the reference broadcasts it (r, notdone
+ *                       (B,1)): loss = mean_{i,j,n} (Q[i,n] - r_j - gamma nd_j Q'[i,n])^2 and
+ *                       dQ[i,n] = 2 / (B B N) sum_j (Q[i,n] - r_j - gamma nd_j Q'[i,n]), in closed form (sums over j in fp64).
+ *                       Q, Q' (B,N); r, notdone (B); either output may be NULL.
+ * mgp_ddpg_policy_loss  loss = -mean Q, dQ = -1 / (B N).
+ * mgp_soft_update       target = target * (1 - tau) + tau * source on flat fp32 buffers: (1 - tau) formed in fp64 then rounded,
+ *                       two fp32 multiplies and one add, unfused -- bit-equal to the reference's torch op sequence.
+ * ------------------------------------------------------------------------------------ */
+int  mgp_ddpg_critic_loss(const float* Q, const float* Qt, const float* r, const float* notdone, float gamma,
+                          float* loss, float* dQ, int B, int N, void* stream);
+int  mgp_ddpg_policy_loss(const float* Q, float* loss, float* dQ, int B, int N, void* stream);
+int  mgp_soft_update(float* target, const float* source, long n, double tau, void* stream);
 
 #ifdef __cplusplus
 }

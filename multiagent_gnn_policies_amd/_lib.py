@@ -137,6 +137,21 @@ SIGNATURES = {
                                   _f32, _f32, _f32, _f32, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     'mgp_train_step': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _f32, _f32, _f32, _f32, _vp,
                               _vp, _vp, _int, _int, _int, _vp]),
+    'mgp_critic_supported': (_int, [ctypes.POINTER(_int), _int, _int, _int, _int]),
+    'mgp_critic_saved_floats': (_long, [ctypes.POINTER(_int), _int, _int, _int, _int]),
+    'mgp_critic_bwd_workspace': (_long, [ctypes.POINTER(_int), _int, _int, _int, _int]),
+    'mgp_critic_fwd': (_int, [_vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                              ctypes.POINTER(_vp), ctypes.POINTER(_int), _int, _int, _vp, _vp, _int, _int, _int, _vp]),
+    'mgp_critic_bwd': (_int, [_vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_int), _int, _int,
+                              ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                              _vp, _vp, _int, _int, _int, _vp]),
+    'mgp_gn_relu_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _f32, _vp]),
+    'mgp_gn_relu_bwd_workspace': (_long, [_int, _int]),
+    'mgp_gn_relu_bwd': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
+    'mgp_tap_sum': (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
+    'mgp_ddpg_critic_loss': (_int, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _int, _int, _vp]),
+    'mgp_ddpg_policy_loss': (_int, [_vp, _vp, _vp, _int, _int, _vp]),
+    'mgp_soft_update': (_int, [_vp, _vp, _long, ctypes.c_double, _vp]),
 }
 
 _lock = threading.Lock()

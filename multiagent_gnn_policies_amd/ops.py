@@ -488,3 +488,201 @@ def adam_step_dev(param, grad, m, v, lr, step_dev, beta1=0.9, beta2=0.999, eps=1
 __all__ = ['MgpFlockParams', 'MgpError', 'aggregate', 'dense', 'agg_fwd', 'agg_bwd_x', 'dense_fwd', 'dense_bwd',
            'gso_update', 'gso_update_into', 'gso_powers', 'flock_step', 'flock_controller', 'mse_grad', 'mse_loss',
            'gso_advance', 'flock_step_advance', 'rollout_supported', 'rollout_steps', 'rollout_collect', 'replay_gather', 'rollout_image', 'rollout_carry_bytes', 'rollout_carry_to_dense', 'adam_step', 'adam_step_dev', 'ACT_NONE', 'ACT_TANH']
+
+
+# ------------------------------------------------------------------------------------ centralized critic (DDPG)
+def _ptrs(ts):
+    return (ctypes.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
+
+
+def _cdims(dims):
+    return (ctypes.c_int * len(dims))(*dims)
+
+
+def critic_supported(dims, B, K, N):
+    """True when the one-launch critic kernels (mgp_critic_fwd / _bwd) cover the shape."""
+    return bool(_lib.lib().mgp_critic_supported(_cdims(dims), len(dims) - 1, B, K, N))
+
+
+class CriticSaved(object):
+    """What critic_forward keeps for critic_backward: `path` is 'fused' (one saved buffer) or 'composed' (per-layer planes)."""
+    __slots__ = ('path', 'saved', 'layers', 'B', 'K', 'N')
+
+
+def critic_forward(states, actions, gso, Ws, bs, gammas, betas, save=True, fused=True):
+    """Critic Q (B,N) of reference critic.py:46-87.  states (B,1,n_s,N), actions (B,1,n_a,N), gso (B,K,N,N); Ws[l] the conv
+    weights (out, K, C_in, 1), bs[l] biases, gammas / betas the GroupNorm affine of the hidden layers.  Returns (Q, saved):
+    saved (save=True) feeds critic_backward.  One launch when mgp_critic_supported covers the shape (and fused=True), else
+    the composed path: per layer mgp_agg_fwd on the input broadcast over the taps, mgp_dense_fwd, mgp_gn_relu_fwd."""
+    _dev(states, 'states'); _dev(actions, 'actions'); _dev(gso, 'gso')
+    B, _, n_s, N = states.shape
+    n_a = actions.shape[2]
+    K = gso.shape[1]
+    dims = [n_s + n_a] + [int(w.shape[0]) for w in Ws]
+    L = _lib.lib()
+    states, actions, gso = states.contiguous(), actions.contiguous(), gso.contiguous()
+    sv = CriticSaved()
+    sv.B, sv.K, sv.N = B, K, N
+    Q = torch.empty((B, N), device=states.device, dtype=torch.float32)
+    if fused and L.mgp_critic_supported(_cdims(dims), len(Ws), B, K, N):
+        saved = torch.empty((L.mgp_critic_saved_floats(_cdims(dims), len(Ws), B, K, N),), device=states.device) if save else None
+        Wc = [w.contiguous() for w in Ws]
+        _lib.check(L.mgp_critic_fwd(_ptr(states), _ptr(actions), _ptr(gso), _ptrs(Wc), _ptrs(bs), _ptrs(gammas),
+                                    _ptrs(betas), _cdims(dims), len(Ws), n_s, _ptr(Q), _ptr(saved), B, K, N, _stream()),
+                   'mgp_critic_fwd')
+        sv.path, sv.saved, sv.layers = 'fused', saved, None
+        return Q, (sv if save else None)
+    x = torch.cat((states.view(B, n_s, N), actions.view(B, n_a, N)), 1)
+    layers = []
+    for l, (W, b_) in enumerate(zip(Ws, bs)):
+        C, O = dims[l], dims[l + 1]
+        Z = torch.empty((B, K, C, N), device=x.device, dtype=torch.float32)
+        _lib.check(L.mgp_agg_fwd(_ptr(x), _ptr(gso), _ptr(Z), B, K, C, N, C * N, 0, N, K * C * N, C * N, N, _stream()),
+                   'mgp_agg_fwd')
+        y = dense_fwd(Z.view(B, K * C, 1, N), W.reshape(O, K * C), b_, ACT_NONE)
+        if l + 1 < len(Ws):
+            a = torch.empty((B, O, N), device=x.device, dtype=torch.float32)
+            mean = torch.empty((B, O), device=x.device, dtype=torch.float32)
+            rstd = torch.empty_like(mean)
+            _lib.check(L.mgp_gn_relu_fwd(_ptr(y), _ptr(gammas[l].contiguous()), _ptr(betas[l].contiguous()), _ptr(a),
+                                         _ptr(mean), _ptr(rstd), B, O, N, 1e-5, _stream()), 'mgp_gn_relu_fwd')
+            layers.append((Z, y, a, mean, rstd))
+            x = a
+        else:
+            Q.copy_(y.view(B, N))
+            layers.append((Z, y, None, None, None))
+    sv.path, sv.saved, sv.layers = 'composed', None, layers if save else None
+    return Q, (sv if save else None)
+
+
+def critic_backward(dQ, gso, sv, Ws, gammas, n_s, want_params=True, want_dactions=False):
+    """Backward of critic_forward from dQ (B,N).  Returns (dWs, dbs, dgammas, dbetas, dActions): parameter gradients summed
+    over the batch (None when want_params is False) and dActions (B,n_a,N) (None unless want_dactions)."""
+    _dev(dQ, 'dQ'); _dev(gso, 'gso')
+    B, K, N = sv.B, sv.K, sv.N
+    dims = [int(Ws[0].shape[2])] + [int(w.shape[0]) for w in Ws]
+    n_a = dims[0] - n_s
+    nl = len(Ws)
+    L = _lib.lib()
+    dev = dQ.device
+    dQ, gso = dQ.contiguous(), gso.contiguous()
+    dWs = [torch.empty(tuple(w.shape), device=dev) for w in Ws] if want_params else None
+    dbs = [torch.empty((w.shape[0],), device=dev) for w in Ws] if want_params else None
+    dgs = [torch.empty_like(g) for g in gammas] if want_params else None
+    dbes = [torch.empty_like(g) for g in gammas] if want_params else None
+    dAct = torch.empty((B, n_a, N), device=dev) if want_dactions else None
+    if sv.path == 'fused':
+        ws = None
+        if want_params:
+            ws = torch.empty((L.mgp_critic_bwd_workspace(_cdims(dims), nl, B, K, N),), device=dev)
+        Wc = [w.contiguous() for w in Ws]
+        _lib.check(L.mgp_critic_bwd(_ptr(dQ), _ptr(gso), _ptr(sv.saved), _ptrs(Wc), _ptrs(gammas), _cdims(dims), nl, n_s,
+                                    _ptrs(dWs) if want_params else None, _ptrs(dbs) if want_params else None,
+                                    _ptrs(dgs) if want_params else None, _ptrs(dbes) if want_params else None,
+                                    _ptr(dAct), _ptr(ws), B, K, N, _stream()), 'mgp_critic_bwd')
+        return dWs, dbs, dgs, dbes, dAct
+    g = dQ.view(B, 1, 1, N)
+    for l in range(nl - 1, -1, -1):
+        C, O = dims[l], dims[l + 1]
+        Z, y, _, _, _ = sv.layers[l]
+        need_dx = l > 0 or want_dactions
+        dW, db, dZ = dense_bwd(g, y, Z.view(B, K * C, 1, N), Ws[l].reshape(O, K * C), ACT_NONE, need_dx)
+        if want_params:
+            dWs[l].view(O, K * C).copy_(dW)
+            dbs[l].copy_(db)
+        if not need_dx:
+            break
+        dX = torch.empty((B, K, C, N), device=dev, dtype=torch.float32)
+        _lib.check(L.mgp_agg_bwd_x(_ptr(dZ), _ptr(gso), _ptr(dX), B, K, C, N, K * C * N, C * N, N, K * C * N, C * N, N,
+                                   _stream()), 'mgp_agg_bwd_x')
+        if l == 0:
+            _lib.check(L.mgp_tap_sum(_ptr(dX), _ptr(dAct), B, K, C, n_s, n_a, N, _stream()), 'mgp_tap_sum')
+            break
+        _, yp, ap, mean, rstd = sv.layers[l - 1]
+        dy = torch.empty((B, C, N), device=dev, dtype=torch.float32)
+        ws = torch.empty((max(1, L.mgp_gn_relu_bwd_workspace(B, C)),), device=dev) if want_params else None
+        _lib.check(L.mgp_gn_relu_bwd(_ptr(dX), K, _ptr(yp), _ptr(ap), _ptr(mean), _ptr(rstd), _ptr(gammas[l - 1].contiguous()),
+                                     _ptr(dy), _ptr(dgs[l - 1]) if want_params else None,
+                                     _ptr(dbes[l - 1]) if want_params else None, _ptr(ws), B, C, N, _stream()),
+                   'mgp_gn_relu_bwd')
+        g = dy.view(B, C, 1, N)
+    return dWs, dbs, dgs, dbes, dAct
+
+
+class _CriticFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, states, actions, gso, fused, nl, *params):
+        Ws, bs = list(params[0:2 * nl:2]), list(params[1:2 * nl:2])
+        gammas, betas = list(params[2 * nl::2]), list(params[2 * nl + 1::2])
+        Q, sv = critic_forward(states, actions, gso, Ws, bs, gammas, betas, save=True, fused=fused)
+        ctx.sv, ctx.nl, ctx.n_s = sv, nl, states.shape[2]
+        ctx.save_for_backward(gso, *Ws, *gammas)
+        return Q
+
+    @staticmethod
+    def backward(ctx, dQ):
+        saved = ctx.saved_tensors
+        nl = ctx.nl
+        gso, Ws, gammas = saved[0], list(saved[1:1 + nl]), list(saved[1 + nl:])
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            raise MgpError("gradients w.r.t. the critic's states / gso are not supported (the reference never asks for them)")
+        want_params = any(ctx.needs_input_grad[5:])
+        want_dact = ctx.needs_input_grad[1]
+        if not (want_params or want_dact):
+            return (None,) * len(ctx.needs_input_grad)
+        dWs, dbs, dgs, dbes, dAct = critic_backward(dQ.contiguous(), gso, ctx.sv, Ws, gammas, ctx.n_s, want_params, want_dact)
+        grads = [None] * (len(ctx.needs_input_grad) - 5)
+        if want_params:
+            for l in range(nl):
+                grads[2 * l], grads[2 * l + 1] = dWs[l], dbs[l]
+            for l in range(nl - 1):
+                grads[2 * nl + 2 * l], grads[2 * nl + 2 * l + 1] = dgs[l], dbes[l]
+        dA = dAct.view(dAct.shape[0], 1, dAct.shape[1], dAct.shape[2]) if want_dact else None
+        return (None, dA, None, None, None, *grads)
+
+
+def critic(states, actions, gso, Ws, bs, gammas, betas, fused=True):
+    """Differentiable (w.r.t. actions and every parameter) critic: Q (B,N)."""
+    params = []
+    for W, b_ in zip(Ws, bs):
+        params += [W, b_]
+    for g, be in zip(gammas, betas):
+        params += [g, be]
+    return _CriticFn.apply(states, actions, gso, fused, len(Ws), *params)
+
+
+def ddpg_critic_loss(Q, Qt, reward, notdone, gamma, loss=None, dQ=None):
+    """The reference's broadcast critic MSE (gnn_ddpg.py:195,200) and its gradient w.r.t. Q; Q, Qt (B,N), reward / notdone
+    (B,).  Returns (loss (1,), dQ (B,N))."""
+    for t, n in ((Q, 'Q'), (Qt, 'Qt'), (reward, 'reward'), (notdone, 'notdone')):
+        _dev(t, n)
+        assert t.is_contiguous()
+    B, N = Q.shape
+    loss = torch.empty((1,), device=Q.device) if loss is None else loss
+    dQ = torch.empty_like(Q) if dQ is None else dQ
+    _lib.check(_lib.lib().mgp_ddpg_critic_loss(_ptr(Q), _ptr(Qt), _ptr(reward), _ptr(notdone), float(gamma), _ptr(loss),
+                                               _ptr(dQ), B, N, _stream()), 'mgp_ddpg_critic_loss')
+    return loss, dQ
+
+
+def ddpg_policy_loss(Q, loss=None, dQ=None):
+    """policy_loss = -mean Q (gnn_ddpg.py:207) and its gradient -1/(B N)."""
+    _dev(Q, 'Q')
+    assert Q.is_contiguous()
+    B, N = Q.shape
+    loss = torch.empty((1,), device=Q.device) if loss is None else loss
+    dQ = torch.empty_like(Q) if dQ is None else dQ
+    _lib.check(_lib.lib().mgp_ddpg_policy_loss(_ptr(Q), _ptr(loss), _ptr(dQ), B, N, _stream()), 'mgp_ddpg_policy_loss')
+    return loss, dQ
+
+
+def soft_update(target, source, tau):
+    """target = target * (1 - tau) + tau * source, in place, bit-equal to the reference's torch ops (gnn_ddpg.py:93-100)."""
+    _dev(target, 'target'); _dev(source, 'source')
+    assert target.is_contiguous() and source.is_contiguous() and target.numel() == source.numel()
+    _lib.check(_lib.lib().mgp_soft_update(_ptr(target), _ptr(source), target.numel(), float(tau), _stream()),
+               'mgp_soft_update')
+
+
+__all__ += ['critic_supported', 'critic_forward', 'critic_backward', 'critic', 'ddpg_critic_loss', 'ddpg_policy_loss',
+            'soft_update']

@@ -7,6 +7,9 @@ line `section, mean, std` per experiment.  Environments come from this package's
 all learning runs on the MI355X kernels.  Under torchrun (one process per GPU) episodes are sharded over the ranks and
 rank 0 prints.  Extensions: `alg = dagger_vec` (device-resident vectorised DAGGER, `n_envs` episodes per GPU);
 `python3 train.py <cfg> --jobs J` runs J sections of the file side by side (same output, file order).
+`alg = ddpg` runs the reference's actor-critic path (learner/gnn_ddpg.py): the cfg section supplies what its argparse did,
+`n_train_episodes` replaces its fixed 10,000 episodes, and the result line is the mean / std of `n_test_episodes` final
+noiseless episodes; the networks are saved only with `debug` and `fname` set.
 """
 import configparser
 import os
@@ -48,7 +51,12 @@ def _dagger_vec(env, args, device):
     return train_dagger_vec(args, device, n_envs=args.getint('n_envs', fallback=64))
 
 
-ALGORITHMS = {'dagger': _dagger, 'cloning': _cloning, 'baseline': _baseline, 'dagger_vec': _dagger_vec}
+def _ddpg(env, args, device):
+    from multiagent_gnn_policies_amd.learner.gnn_ddpg import train_ddpg
+    return train_ddpg(env, args, device)
+
+
+ALGORITHMS = {'dagger': _dagger, 'cloning': _cloning, 'baseline': _baseline, 'dagger_vec': _dagger_vec, 'ddpg': _ddpg}
 
 
 def check_experiment(args):
